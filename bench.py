@@ -28,6 +28,11 @@ transitions PPO trains on are counted, as completed (a rollout that ran out of t
 `short_rollouts`). `--lockstep` runs the classic vector-env schedule for comparison.
 Workload = BASELINE.json configs[1]: acorn_env (labelled stand-in hull: the reference checkout has no acorn.stl), 4096 envs per GPU,
 direction 0, default flags. Weak scaling: per-GPU work is fixed as N grows. Defaults: 20 warm-up + 200 timed steps.
+
+A plain run does only what the headline figure needs: set-up, priming, pre-roll, warm-up, the K timed steps and the JSON line.
+`--full` adds the measurements of their own: the CPU baseline (the C oracle and the policy on the host cores, `cpu_baseline`; N = 1).
+`--dump-outputs DIR` writes what the timed path computed in its last step as DIR/<name>.npy (see dump_outputs()); such a run caps its time
+slices by their physics.step() count only, not by wall-clock time, so that the same arguments compute the same outputs every time.
 """
 import argparse
 import json
@@ -126,6 +131,96 @@ def cpu_baseline(obj, seconds_target=15.0):
             "note": "reference dm_control+SB3 stack cannot be installed here; its recorded whole-training rate is 3.95-12.97 env-steps/s (BASELINE.md)"}
 
 
+DUMP_MAX_BYTES = 64 << 20
+DUMP_MAX_RECORDS = 1 << 17          # records kept in full; beyond that, a fixed, seeded choice of positions among them
+DUMP_OBS_ROWS = 128
+
+
+def dump_outputs(out_dir, model, ar, last, seed):
+    """--dump-outputs DIR: what the timed path computed in its last step -- the transitions of the last rollout that the last PPO update
+    trained on, with their GAE advantages and returns, that update's losses, and the policy's parameters after it -- as DIR/<name>.npy:
+
+      record_env, record_t        float64 [M]   env index and the env's decision counter t of each record (records sorted by env, then t)
+      actions                     float32 [M, 6]
+      rewards, dones, values, log_probs, advantages, returns   float32 [M]
+      obs_sample, obs_sample_env, obs_sample_t   float32 [m, 5, 64, 64], float64 [m]: the observations of the records at m fixed, seeded
+                                  positions of that list (m = min(M, DUMP_OBS_ROWS))
+      policy_params               float32 [P]   every parameter of the policy, flattened in module order
+      loss, policy_loss, value_loss   float64 [1]   of the last minibatch of the last update
+
+    Every shape follows from the arguments alone: M = the transitions the last update trains on (--envs x the last rollout's length), or
+    DUMP_MAX_RECORDS of them at fixed, seeded positions when there are more. A rollout that ran out of ticks (`short_rollouts`) fills its
+    missing rows with zeros and env = t = -1.
+    Reproducible: with --dump-outputs the time slices are capped by their physics.step() count only, not by wall-clock time (--budget-us and
+    the slice ladder's budgets, which decide which macro steps finish in a tick and so which transitions a rollout holds), so the same
+    arguments give the same outputs in every run; each env's physics does not depend on where a slice ends.
+    t: with the synthetic action stream (the default) the counter the stream is keyed by; with policy-sampled actions t counts back from the
+    env's last decision (-1 = the decision still in flight); lock-step: the step within the last rollout. Each file is float32 or float64, all
+    of them at most DUMP_MAX_BYTES together."""
+    dev = model.device
+    with torch.no_grad():
+        if ar is not None:
+            lo = ar.carry0                                                           # the records the last update trained on (AsyncRollout.training_indices)
+            n_rec = last["target"]
+            sel = (ar.completed[lo:lo + ar.W] & ar.is_rec[lo:lo + ar.W]).nonzero().flatten()[:n_rec] + lo
+            back = torch.full((ar.R + 1,), -1, dtype=torch.int64, device=dev)        # steps back from the env's in-flight record
+            cur = ar.rec_of_env[:ar.N].clone()
+            for k in range(ar.max_ticks + 2):                                        # every record of the window lies on its env's chain
+                live = cur >= 0
+                if not bool(live.any()):
+                    break
+                back[cur[live]] = k
+                cur = torch.where(live, ar.prev_rec[cur.clamp(min=0)], torch.full_like(cur, -1))
+            env = ar.rec_env[sel]
+            t = ar.rng_count[env] - 1 - back[sel]
+            rec = {"actions": ar.actions[sel], "rewards": ar.rewards[sel], "dones": ar.dones[sel], "values": ar.values[sel],
+                   "log_probs": ar.log_probs[sel], "advantages": ar.advantages[sel], "returns": ar.returns[sel]}
+            obs_rows = ar.obs[sel]
+        else:
+            buf, T = model.rollout_buffer, last["T"]
+            n = buf.n_envs; n_rec = T * n
+            env = torch.arange(n, device=dev).repeat(T); t = torch.arange(T, device=dev).repeat_interleave(n)
+            rec = {"actions": buf.actions[:T].reshape(T * n, -1)}
+            for name in ("rewards", "dones", "values", "log_probs", "advantages", "returns"):
+                rec[name] = getattr(buf, name)[:T].reshape(-1)
+            obs_rows = buf.obs[:T].reshape((T * n,) + tuple(buf.obs.shape[2:]))
+        env_h = env.cpu().numpy().astype(np.int64); t_h = t.cpu().numpy().astype(np.int64)
+        rows = np.full(n_rec, -1, np.int64)                       # -1: a row a short rollout did not complete
+        got = np.lexsort((t_h, env_h))[:n_rec]
+        rows[:got.size] = got
+        if n_rec > DUMP_MAX_RECORDS:
+            rows = rows[np.sort(np.random.default_rng(seed).choice(n_rec, size=DUMP_MAX_RECORDS, replace=False))]
+
+        def take(src, r):                                         # device rows -> float32 host array, zeros for the -1 rows
+            out = np.zeros((r.size,) + tuple(src.shape[1:]), np.float32)
+            ok = r >= 0
+            if ok.any():
+                out[ok] = src[torch.from_numpy(r[ok]).to(dev)].float().cpu().numpy()
+            return out
+
+        def keys(r):
+            ok = r >= 0
+            return (np.where(ok, env_h[r.clip(0)], -1).astype(np.float64) if env_h.size else np.full(r.size, -1.0),
+                    np.where(ok, t_h[r.clip(0)], -1).astype(np.float64) if t_h.size else np.full(r.size, -1.0))
+
+        arrays = dict(zip(("record_env", "record_t"), keys(rows)))
+        for name, v in rec.items():
+            arrays[name] = take(v, rows)
+        obs_r = rows[np.sort(np.random.default_rng(seed + 1).choice(rows.size, size=min(rows.size, DUMP_OBS_ROWS), replace=False))]
+        arrays["obs_sample"] = take(obs_rows, obs_r)
+        arrays["obs_sample_env"], arrays["obs_sample_t"] = keys(obs_r)
+        arrays["policy_params"] = torch.cat([p.detach().float().flatten() for p in model.policy.parameters()]).cpu().numpy()
+        for name in ("loss", "policy_loss", "value_loss"):
+            v = (last.get("stats") or {}).get(name)
+            arrays[name] = np.array([float("nan") if v is None else float(v)], np.float64)
+    total = sum(v.nbytes for v in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        raise RuntimeError(f"bench.py: --dump-outputs would write {total} bytes, more than {DUMP_MAX_BYTES}")
+    os.makedirs(out_dir, exist_ok=True)
+    for name, v in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), v)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -137,7 +232,10 @@ def main():
     ap.add_argument("--rollout", type=int, default=8, help="PPO n_steps (rollout length per env)")
     ap.add_argument("--epochs", type=int, default=2)
     ap.add_argument("--minibatch", type=int, default=4096)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true", help="also run the measurements of their own: the CPU baseline (cpu_baseline, N = 1)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the timed path computed in its last step as DIR/<name>.npy (dump_outputs()); "
+                                                                     "such a run is reproducible: its time slices are not capped by wall-clock time")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baseline out")
     ap.add_argument("--no-ppo", action="store_true", help="diagnostic: rollout only (INVALID as a headline number)")
     ap.add_argument("--lockstep", action="store_true", help="classic vector-env schedule instead of asynchronous time slices")
     ap.add_argument("--state-dtype", choices=["f32", "f16"], default="f32", help="HBM storage of qpos / qvel / ctrl (BASELINE.json configs[4]: f16; arithmetic is always f32)")
@@ -156,6 +254,8 @@ def main():
     ap.add_argument("--preroll", type=int, default=800, help="untimed rollout-only steps before the warm-up: desynchronised, mixed episode phases")
     ap.add_argument("--seed", type=int, default=0)
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        raise SystemExit("--steps must be at least 1 and --warmup at least 0")
     if a.capacity <= 0:
         a.capacity = max(8, (3 * a.envs // 8) // 8 * 8)
     if a.actions is None:
@@ -218,6 +318,12 @@ def main():
     if a.state_dtype == "f16":
         batch.set_state_storage("f16")
     ar = model._async
+    if ar is not None and a.dump_outputs:
+        # a run that dumps its outputs must compute the same from the same arguments every time (dump_outputs()): its slices are capped by
+        # their physics.step() count alone (the same slice ladder), never by wall-clock time, which decides which macro steps finish in a tick
+        ar.eng.budget_us = 0
+        if ar.ladder:
+            ar.set_slice_ladder(tuple((m, sl, 0) for m, sl, _ in ar.ladder))
     if ar is not None and a.pipeline:
         ar.enable_pipeline()
     if a.actions == "rng":
@@ -225,6 +331,7 @@ def main():
             raise SystemExit("--actions rng needs the time-sliced schedule (the fused recorder draws the stream); use --actions policy with --lockstep")
         ar.set_synthetic_actions(a.seed, rank)
     counted = {"done": 0, "short": 0}
+    last = {"stats": None, "T": a.rollout, "target": a.rollout * a.envs}       # the last update's losses, rollout length and target (dump_outputs)
 
     def run_async(nsteps, train=True):
         """nsteps x envs completed transitions, a PPO update after every `rollout` x envs of them (a shorter last rollout is
@@ -232,13 +339,13 @@ def main():
         done_steps = 0
         while done_steps < nsteps:
             chunk = min(a.rollout, nsteps - done_steps)
-            ar.set_target(chunk * a.envs); model.n_steps = chunk
+            ar.set_target(chunk * a.envs); model.n_steps = chunk; last["target"] = ar.target
             before = model.num_timesteps
             model.collect_rollouts()
             got = model.num_timesteps - before                  # transitions that really completed (polled on the device counter)
             counted["done"] += min(got, ar.target); counted["short"] += int(got < ar.target)
             if train and not a.no_ppo:
-                model.train()
+                last["stats"] = model.train()
             done_steps += chunk
         ar.set_target(a.rollout * a.envs); model.n_steps = a.rollout
 
@@ -254,8 +361,8 @@ def main():
             model.collect_rollouts()
             counted["done"] += chunk * a.envs
             if train and not a.no_ppo:
-                model.train()
-            done_steps += chunk
+                last["stats"] = model.train()
+            done_steps += chunk; last["T"] = chunk
         model.n_steps = a.rollout; model.rollout_buffer.n_steps = a.rollout
 
     def sync():
@@ -342,6 +449,8 @@ def main():
         if d_n > 0:
             k_ms, k_n = d_ms, int(d_n)
     ar_ms, ar_n = (model.allreduce_ms() if (world > 1 and hasattr(model, "allreduce_ms")) else (None, 0))
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, model, ar, last, a.seed)
 
     if rank == 0:
         value = total_env_steps / dt            # transitions that completed and were trained on, all ranks / max-over-ranks time
@@ -360,7 +469,7 @@ def main():
             overhead_bytes = (2 * (32 + 64) + 2 * 16 * 16 + 2 * 48 // 2) * a.envs
         macro_bytes = state_bytes * a.envs + int(fin_per_launch * (24 + 85))
         sched = ("lock-step vector env" if ar is None else
-                 f"asynchronous time slices (<= {ar.S} physics steps and <= {ar.eng.budget_us} us per wavefront and tick"
+                 f"asynchronous time slices (<= {ar.S} physics steps and " + (f"<= {ar.eng.budget_us} us" if ar.eng.budget_us > 0 else "no wall-clock cap") + " per wavefront and tick"
                  + (f" at the end of the run: slice / budget follow the measured macro-step length, {ar.ladder}" if ar.ladder else "")
                  + f", {min(a.capacity, a.envs)} decisions/tick)" + ("; comparison build: cold-started portal refinement" if a.cold_portal else "") + ("; PPO update overlapped with the next rollout (policy lag 1)" if a.overlap_update else ""))
         achieved = macro_bytes / (k_ms * 1e-3) / 1e9 if k_ms > 0 else 0.0
@@ -447,7 +556,7 @@ def main():
                                   "source": f"profiles/{pmc_file} (SQ_INSTS_VALU per launch of the same command) / live launch duration"}
             except Exception:
                 pass
-        if not a.no_cpu_baseline and world == 1:
+        if a.full and not a.no_cpu_baseline and world == 1:
             try:
                 out["cpu_baseline"] = cpu_baseline(a.object)
             except Exception as ex:      # the oracle is optional test infrastructure

@@ -231,9 +231,9 @@ def test_eval_agent_loop_shape(torch, tmp_path):
     env.close()
 
 
-@pytest.mark.parametrize("extra", [[], ["--lockstep", "--no-cpu-baseline"], ["--overlap-update", "--no-cpu-baseline"]])
+@pytest.mark.parametrize("extra", [["--full"], ["--lockstep", "--no-cpu-baseline"], ["--overlap-update", "--no-cpu-baseline"]])
 def test_bench_json_contract(torch, extra):
-    """bench.py prints exactly one JSON line with the driver's keys, the roofline object and (N = 1) the cpu baseline."""
+    """bench.py prints exactly one JSON line with the driver's keys, the roofline object and (N = 1, --full) the cpu baseline."""
     import json, os, subprocess, sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--envs", "256", "--steps", "4", "--warmup", "2", "--rollout", "2", "--minibatch", "256",
@@ -251,9 +251,64 @@ def test_bench_json_contract(torch, extra):
     for k in ("bound", "achieved", "peak", "unit", "frac", "traffic"):
         assert k in d["roofline"], k
     assert abs(d["roofline"]["frac"] - d["roofline"]["achieved"] / d["roofline"]["peak"]) < 1e-12
-    if "--no-cpu-baseline" not in extra:
+    if "--full" in extra and "--no-cpu-baseline" not in extra:
         for k in ("value", "unit", "cores", "kind", "sample"):
             assert k in d["cpu_baseline"], k
+
+
+@pytest.mark.parametrize("extra", [[], ["--lockstep"]])
+def test_bench_dump_outputs(torch, tmp_path, extra):
+    """A plain bench.py run (no --full) measures the headline only, runs exactly --steps timed steps, and with --dump-outputs DIR writes what the
+    timed path computed in its last step: float32 / float64 .npy files, 64 MB at most, shapes set by the arguments alone, the records keyed by
+    (env, t) without repeats."""
+    import json, os, subprocess, sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out = tmp_path / "dump"
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--envs", "256", "--steps", "3", "--warmup", "1", "--rollout", "2", "--minibatch", "256",
+           "--capacity", "64", "--object", "sand_ball", "--preroll", "4", "--dump-outputs", str(out)] + extra
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=280)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    assert d["steps"] == 3 and d["env_steps_nominal"] == 3 * 256 and d["ms_per_step"] > 0 and "cpu_baseline" not in d
+    files = {f[:-4]: np.load(out / f) for f in os.listdir(out)}
+    assert sum(v.nbytes for v in files.values()) <= 64 << 20
+    assert all(v.dtype in (np.float32, np.float64) for v in files.values())
+    for k in ("record_env", "record_t", "actions", "rewards", "dones", "values", "log_probs", "advantages", "returns", "obs_sample", "policy_params", "loss"):
+        assert k in files, k
+    m = files["record_env"].shape[0]
+    assert files["actions"].shape == (m, 6) and files["returns"].shape == (m,)
+    assert m == 256                                       # shapes follow from the arguments: --steps 3 with --rollout 2 ends on a 1-step rollout of 256 envs
+    done = files["record_env"] >= 0                       # (rows a short rollout did not complete are zeros keyed -1)
+    assert done.sum() == 256 or d["short_rollouts"] > 0
+    assert len(set(zip(files["record_env"][done].tolist(), files["record_t"][done].tolist()))) == int(done.sum()) > 0
+    assert files["obs_sample"].shape == (128, 5, 64, 64) and files["obs_sample_env"].shape == (128,) and files["obs_sample"].any()
+    assert np.isfinite(files["loss"]).all() and np.isfinite(files["policy_params"]).all()
+
+
+def test_bench_dump_outputs_repeat(torch, tmp_path):
+    """Two bench.py runs with the same arguments and --dump-outputs compute the same outputs: the time-sliced schedule of a dumping run is capped by
+    physics.step() counts, not by wall-clock time, so the same transitions reach the same updates. Records, actions, rewards, dones and
+    observations agree exactly; what the policy and the update computed from them to within rounding."""
+    import os, subprocess, sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    got = []
+    for k in range(2):
+        out = tmp_path / f"dump{k}"
+        cmd = [sys.executable, os.path.join(root, "bench.py"), "--envs", "512", "--steps", "5", "--warmup", "2", "--rollout", "2", "--minibatch", "512",
+               "--capacity", "128", "--object", "sugar_cube", "--preroll", "40", "--dump-outputs", str(out)]
+        r = subprocess.run(cmd, capture_output=True, text=True, timeout=280)
+        assert r.returncode == 0, r.stderr[-2000:]
+        got.append({f[:-4]: np.load(out / f) for f in os.listdir(out)})
+    a, b = got
+    assert a.keys() == b.keys()
+    for k in a:
+        assert a[k].shape == b[k].shape, k
+        if k in ("record_env", "record_t", "actions", "rewards", "dones", "obs_sample", "obs_sample_env", "obs_sample_t"):
+            assert np.array_equal(a[k], b[k]), k
+        else:
+            assert np.allclose(a[k], b[k], rtol=1e-5, atol=1e-6), (k, float(np.abs(a[k] - b[k]).max()))
 
 
 def test_integration_md_ctypes_stub_runs(torch):

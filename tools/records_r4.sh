@@ -6,7 +6,7 @@ set -e
 tag=$1; quick=$2
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 out=gpurun_out/$tag; mkdir -p $out
-python bench.py > $out/default.json 2> $out/default.err
+python bench.py --full > $out/default.json 2> $out/default.err
 python bench.py --steps 20 --warmup 5 --no-cpu-baseline > $out/steps20_warmup5.json 2>/dev/null
 python tools/physics_rate.py - acorn 144 3000 1500 2048 > $out/physics_rate.json 2>/dev/null
 echo bench-done
